@@ -25,7 +25,19 @@ sized so one gathered chunk fits --gather-budget-gb on rank 0
 --shards independent replica groups of --shards subscriber shards each (own
 process group, own batch, own leader).
 
-Rank 0 prints ONE JSON line.  `roofline.achieved` = algorithmic bytes of the
+A run sets up (the workload read back from tools/_build/workloads when
+build() or an earlier run wrote it, mqgen.generate_cached; the index built in
+a child process whose malloc uses transparent huge pages,
+spawn_with_huge_pages), warms up, times --steps steps, writes the last step's
+outputs with --dump-outputs DIR (dump_match_outputs) and prints the result
+line: `value`, `ms_per_step` and the counters of the timed steps.  Everything
+else is measured only with --full, after the timed region: per-stage kernel
+times of isolated batches (`kernel_ms`), `roofline`, `cpu_baseline`,
+`host_path` / `end_to_end`, `steady_state`, `single_topic_latency`,
+`identifiers`, `gather_proxy` (reverse: `selfcheck`, `cpu_baseline`); without
+it those fields are null.
+
+Rank 0 prints ONE JSON line.  (--full) `roofline.achieved` = algorithmic bytes of the
 match pipeline (B = T + 8N + 8P + 8V + 8S + 8D, per-topic walk
 counters from the oracle on the CPU sample) / its HIP-event time per batch.
 `cpu_baseline` = oracle/mochi_ref.c (C restatement of the reference matcher,
@@ -53,6 +65,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements (per-kernel times of isolated "
+                         "batches, host path, steady state, latency, Identifiers leg, CPU baseline and the roofline "
+                         "it feeds; reverse: self-check and CPU baseline); a run without it only sets up, warms up, "
+                         "times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last timed step returned as DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of the topics, see dump_outputs)")
     ap.add_argument("--config", type=int, default=3, help="BASELINE configs index + 1 (mqgen config)")
     ap.add_argument("--filters", type=int, default=0, help="override n_filters")
     ap.add_argument("--topics", type=int, default=0, help="override n_topics")
@@ -166,6 +186,34 @@ def spawn_ranks(args):
     return subprocess.call(cmd, env=env)
 
 
+HUGE_PAGES = "glibc.malloc.hugetlb=1"
+
+
+def spawn_with_huge_pages():
+    """Run this benchmark in a child process whose malloc asks for transparent
+    huge pages (glibc >= 2.35 reads GLIBC_TUNABLES at program start only; an
+    older glibc ignores the tunable).  The host store's build of the index is
+    bound by page faults and TLB misses over its tables (10M Subscribes: 27 s
+    -> 22 s on one box); nothing on the device changes.  Runs before anything
+    touches the GPU; the child ends with this process (signals are passed on)."""
+    import ctypes
+    import signal
+    import subprocess
+
+    env = dict(os.environ)
+    env["GLIBC_TUNABLES"] = ":".join(x for x in (env.get("GLIBC_TUNABLES", ""), HUGE_PAGES) if x)
+
+    def die_with_parent():
+        ctypes.CDLL(None).prctl(1, signal.SIGKILL)  # PR_SET_PDEATHSIG
+
+    child = subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env,
+                             preexec_fn=die_with_parent)
+    for sig in (signal.SIGTERM, signal.SIGINT, signal.SIGHUP):
+        signal.signal(sig, lambda s, _f: child.send_signal(s))
+    rc = child.wait()
+    return rc if rc >= 0 else 128 - rc  # (ended by a signal: the shell's convention)
+
+
 def cpu_threads(args):
     """one thread per CPU this process may actually run on —
     its affinity mask, capped by its cgroup CPU quota (the GPU box grants a
@@ -216,6 +264,8 @@ def host_info():
 
 def main():
     args = parse()
+    if "WORLD_SIZE" not in os.environ and HUGE_PAGES not in os.environ.get("GLIBC_TUNABLES", ""):
+        sys.exit(spawn_with_huge_pages())
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     _heartbeat()
@@ -260,8 +310,8 @@ def main():
         w = shard.generated_shard(args.config, k, my_shard, **overrides)
     elif shard_of:
         w = shard.generated_shard(args.config, shard_of[1], shard_of[0], **overrides)
-    else:
-        w = mqgen.generate(args.config, **overrides)
+    else:  # (read back from tools/_build/workloads when an earlier run or build() generated it)
+        w = mqgen.generate_cached(args.config, **overrides)
     n = len(w.topics)
     log(f"[rank {rank}] generated {len(w.filters)} filters / {n} topics in {time.time() - t0:.1f}s")
 
@@ -354,9 +404,10 @@ def main():
         pipe["k"] = 0
 
     def drain():
-        """pipelined steps: wait for every batch still in flight (their results)"""
+        """pipelined steps: wait for every batch still in flight, oldest first
+        (their results, the batch submitted last at the end)"""
         out = []
-        for c in range(args.pipeline):
+        for c in ((pipe["k"] + i) % args.pipeline for i in range(args.pipeline)):
             if pipe["pend"][c]:
                 out.append(pipe["ctxs"][c].wait())
                 pipe["pend"][c] = False
@@ -390,9 +441,10 @@ def main():
         step()
     if pipe:
         drain()
-        # the index's own workspace (the isolated batches timed per stage after
-        # the timed region) sized now, so those batches allocate nothing
-        idx.match_device(tb.data_ptr(), to.data_ptr(), n, stream.cuda_stream)
+        if args.full:
+            # the index's own workspace (the isolated batches timed per stage after
+            # the timed region) sized now, so those batches allocate nothing
+            idx.match_device(tb.data_ptr(), to.data_ptr(), n, stream.cuda_stream)
     torch.cuda.synchronize(dev)
     if args.sweep:
         run_sweep(args, idx, step, dev, rank)
@@ -427,7 +479,12 @@ def main():
     if dist:
         dist.barrier()
     dt = time.perf_counter() - t0
-    if pipe:
+    if args.dump_outputs and rank == 0:
+        # (the last entry of `results` is the batch submitted last: its buffers
+        # stay valid until that context's / the index's next match)
+        last = results[-1] if results else (None, 0, 0)
+        dump_match_outputs(args.dump_outputs, last[0], n, dev, totals=(n, last[1], last[2]))
+    if pipe and args.full:
         # kernel times of the stages: isolated (blocking) batches on the index's
         # own workspace after the timed region (the pipelined contexts overlap
         # batches, so a batch has no device time of its own there)
@@ -459,20 +516,22 @@ def main():
     out = None
     if rank == 0:
         calls = max(prof["calls"], 1)
-        kms = {k: prof[f"{k}_ms"] / calls for k in ("walk", "dedupe", "total")}
+        # (pipelined steps without --full: no isolated batches ran, the stages have no times)
+        kms = {k: prof[f"{k}_ms"] / calls if args.full or not pipe else None for k in ("walk", "dedupe", "total")}
         cpu = None
         stats = None
         # per-GPU side measurements at N = 1 only (the contract's cpu_baseline
         # leg; host path and latency are per-GPU properties too); at N > 1 the
         # oracle runs only a short sample for the roofline's algorithmic bytes
-        host = host_path(idx, w, args, "runs") if args.host_topics and world == 1 else None
+        side = args.full and world == 1
+        host = host_path(idx, w, args, "runs") if args.host_topics and side else None
         if host:
             host["packed"] = host_path(idx, w, args, "packed")
-        steady = steady_state(idx, tb, to, n, dev, args) if world == 1 and not shard_of and args.steady_steps else None
-        gproxy = gather_proxy(idx, tb, to, n, dev, args, shard_of[1]) if world == 1 and shard_of else None
-        lat = latency(idx, w, args) if args.latency_topics and world == 1 else None
-        ident = identifiers_leg(idx, tb, to, n, dev, args) if args.ident_steps and world == 1 else None
-        if not args.no_cpu_baseline:
+        steady = steady_state(idx, tb, to, n, dev, args) if side and not shard_of and args.steady_steps else None
+        gproxy = gather_proxy(idx, tb, to, n, dev, args, shard_of[1]) if side and shard_of else None
+        lat = latency(idx, w, args) if args.latency_topics and side else None
+        ident = identifiers_leg(idx, tb, to, n, dev, args) if args.ident_steps and side else None
+        if args.full and not args.no_cpu_baseline:
             if world == 1:
                 cpu, stats = cpu_baseline(w, args)
             else:
@@ -493,6 +552,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": dt * 1e3 / args.steps,
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "strong" if sharded and len(groups) == 1 else "weak",
             "vs_baseline": None,
@@ -521,7 +581,7 @@ def main():
             "big_topics_per_batch": big,
             "fallback_reasons": why,
             "emit_lists": lists,
-            "kernel_ms": kms,
+            "kernel_ms": kms if kms["total"] is not None else None,
             "snapshot": snap,
             "roofline": roof,
             "cpu_baseline": cpu,
@@ -542,6 +602,125 @@ def main():
     if dist:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_SEED = 0x4D51D0  # --dump-outputs: the sampled segments (topics / filters) are a seeded choice
+DUMP_SEGMENTS = 16384
+DUMP_MAX_ENTRIES = 6000000  # entries of the sampled segments kept per list (float64: 48 MB)
+DUMP_BLOCK = 256  # segments per entry of the whole-batch count sums
+
+
+def _sampled_segments(starts, counts, ents, sample, max_entries, mask=None):
+    """The sampled segments of a device CSR (int64 tensors: starts / counts
+    [n], `sample` ascending segment indices; ents the entries, any integer
+    dtype, `mask` its value bits): each segment's entries sorted ascending (the
+    order inside a segment is unspecified), concatenated in sample order.
+    Segments past the first `max_entries` entries are left out.  -> (segments
+    kept, their counts, the entries), float64 numpy arrays."""
+    import torch
+
+    st, ct = starts[sample], counts[sample]
+    cum = torch.cumsum(ct, 0)
+    keep = int((cum <= max_entries).sum())
+    sample, st, ct, cum = sample[:keep], st[:keep], ct[:keep], cum[:keep]
+    total = int(cum[-1]) if keep else 0
+    seg = torch.repeat_interleave(torch.arange(keep, device=starts.device), ct)
+    src = st[seg] + torch.arange(total, device=starts.device) - (cum - ct)[seg]
+    vals = ents[src].to(torch.int64)
+    if mask is not None:
+        vals = vals & mask
+    vals, order = torch.sort(vals, stable=True)
+    vals = vals[torch.sort(seg[order], stable=True).indices]
+    return tuple(t.to(torch.float64).cpu().numpy() for t in (sample, ct, vals))
+
+
+def _block_sums(counts):
+    """sums of `counts` (int64 tensor [n]) over blocks of DUMP_BLOCK segments: the whole batch, coarsely"""
+    import torch
+
+    nb = (counts.numel() + DUMP_BLOCK - 1) // DUMP_BLOCK
+    pad = torch.zeros(nb * DUMP_BLOCK, dtype=torch.int64, device=counts.device)
+    pad[: counts.numel()] = counts
+    return pad.view(nb, DUMP_BLOCK).sum(1).to(torch.float64).cpu().numpy()
+
+
+def _dump_sample(n, dev):
+    import torch
+
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = np.sort(rng.choice(n, size=min(n, DUMP_SEGMENTS), replace=False)).astype(np.int64)
+    return torch.from_numpy(pick).to(dev)
+
+
+def dump_match_outputs(out_dir, r, n, dev, totals):
+    """--dump-outputs of the forward workload: what the last timed step's
+    mqm_device_result holds, as float64 .npy files.  The whole result (about
+    64 deliveries per topic over 10M topics) is too large to write, so:
+      totals.npy                  [topics, deliveries, shared candidates] of the step
+      counts_by_block.npy         deliveries of every DUMP_BLOCK consecutive topics (all topics)
+      shared_counts_by_block.npy  shared candidates, the same way
+      sample_topics.npy           DUMP_SEGMENTS topic indices, a seeded choice, ascending
+      counts.npy / deliveries.npy per sampled topic its delivery count and its packed
+                                  deliveries (mqm_delivery `packed`), sorted inside the topic
+                                  (the library leaves that order open), concatenated
+      shared_topics.npy / shared_counts.npy / shared.npy  the same for the shared candidates
+    A list is cut at DUMP_MAX_ENTRIES entries (whole topics; *_topics.npy
+    names the ones kept); lists without any entry (the shared files of a
+    workload without $SHARE filters) are not written.  A sharded node step returns no single result:
+    only totals.npy is written."""
+    import torch
+
+    from maxmq_amd.devbuf import dev_view_copy
+
+    os.makedirs(out_dir, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, np.float64))  # noqa: E731
+    save("totals", totals)
+    if r is None:
+        return
+    u32 = 0xFFFFFFFF
+    sample = _dump_sample(n, dev)
+    for starts_p, counts_p, ents_p, names, cap in (
+            (r.starts, r.counts, r.deliveries, ("sample_topics", "counts", "deliveries", "counts_by_block"),
+             DUMP_MAX_ENTRIES),
+            (r.shared_starts, r.shared_counts, r.shared,
+             ("shared_topics", "shared_counts", "shared", "shared_counts_by_block"), DUMP_MAX_ENTRIES // 6)):
+        starts = dev_view_copy(starts_p, n, torch.int64, dev)
+        counts = dev_view_copy(counts_p, n, torch.int32, dev).to(torch.int64) & u32
+        torch.cuda.synchronize(dev)
+        if not int(counts.sum()):  # (no $SHARE filters, no shared candidates: totals.npy says so, no files of zeros)
+            continue
+        extent = int((starts + counts).max()) if n else 0  # (segments may leave gaps)
+        ents = dev_view_copy(ents_p, extent, torch.int32, dev)
+        kept, cnt, vals = _sampled_segments(starts, counts, ents, sample, cap, mask=u32)
+        for name, a in zip(names, (kept, cnt, vals, _block_sums(counts))):
+            if len(a):  # (a workload without $SHARE filters has no shared candidates: no empty file)
+                save(name, a)
+        del ents
+    log(f"[bench] outputs of the last timed step written to {out_dir}")
+
+
+def dump_reverse_outputs(out_dir, m, n, dev):
+    """--dump-outputs of the reverse workload: the last timed step's
+    mqm_device_messages as float64 .npy files: totals.npy [filters, refs],
+    counts_by_block.npy (refs of every DUMP_BLOCK consecutive filters), and for
+    a seeded sample of the filters sample_filters.npy, counts.npy and refs.npy
+    (each filter's refs sorted, concatenated; cut at DUMP_MAX_ENTRIES)."""
+    import torch
+
+    from maxmq_amd.devbuf import dev_view_copy
+
+    os.makedirs(out_dir, exist_ok=True)
+    save = lambda name, a: np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, np.float64))  # noqa: E731
+    save("totals", [n, int(m.n_refs)])
+    offs = dev_view_copy(m.offsets, n + 1, torch.int64, dev)
+    refs = dev_view_copy(m.refs, int(m.n_refs), torch.int64, dev)
+    torch.cuda.synchronize(dev)
+    counts = offs[1:] - offs[:-1]
+    kept, cnt, vals = _sampled_segments(offs[:-1], counts, refs, _dump_sample(n, dev), DUMP_MAX_ENTRIES)
+    for name, a in zip(("sample_filters", "counts", "refs", "counts_by_block"), (kept, cnt, vals, _block_sums(counts))):
+        if len(a):
+            save(name, a)
+    log(f"[bench] outputs of the last timed step written to {out_dir}")
 
 
 def identifiers_leg(idx, tb, to, n, dev, args):
@@ -1268,10 +1447,12 @@ def run_reverse(args, dist, rank, world, local, dev):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # full-size property check, outside the timed region: the same call twice
-    # gives the same per-filter counts and the same checksum of every filter's
-    # refs (order-independent: sum of mixed refs per filter)
-    check = reverse_selfcheck(idx, fb, fo, n, dev, stream)
+    if args.dump_outputs and rank == 0:
+        dump_reverse_outputs(args.dump_outputs, r, n, dev)
+    # (--full) full-size property check, outside the timed region: the same call
+    # twice gives the same per-filter counts and the same checksum of every
+    # filter's refs (order-independent: sum of mixed refs per filter)
+    check = reverse_selfcheck(idx, fb, fo, n, dev, stream) if args.full else None
     if rank == 0:
         steps = args.steps
         tbytes = int(w.filters.offs[-1])
@@ -1294,7 +1475,7 @@ def run_reverse(args, dist, rank, world, local, dev):
             except Exception:
                 traffic = None
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             cpu = cpu_reverse(w, refs, args)
         out = {
             "metric": "retained reverse match: filters matched/sec + retained hits/sec",
@@ -1304,6 +1485,7 @@ def run_reverse(args, dist, rank, world, local, dev):
             "steps": steps,
             "warmup": args.warmup,
             "ms_per_step": dt * 1e3 / steps,
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
